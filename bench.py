@@ -7,16 +7,21 @@ records are gathered over RCCL (config 4).  Inputs are resident in HBM before th
 each in-flight context segments its own batch (distinct frames, no cross-batch cache reuse).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-gpu B] [--settle-steps S]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 The K timed steps are bracketed by a barrier and torch.cuda.synchronize() on both sides and timed as
-the max over ranks.  The same K-step window is timed twice: first after only the W warm-up steps (the
-GPU from idle: `value_without_settle`), then after S untimed pipelined settle steps (default 300,
-~0.2 s) and the W warm-up steps again (`value`): the first tens of milliseconds of pipelined work after
-an idle GPU run ~10 % slower per step.  `untimed_steps` counts every pipelined step
-run before the timed window.
+the max over ranks, after S untimed pipelined settle steps (default 300, ~0.2 s) and the W warm-up
+steps (`value`): the first tens of milliseconds of pipelined work after an idle GPU run ~10 % slower
+per step.  `untimed_steps` counts every pipelined step run before the timed window.
 
-Prints ONE JSON line on rank 0.  Besides the headline value it carries (rank 0, N = 1):
+A plain run does only that: set up, settle and warm up, time the K steps, write the outputs of the
+last timed step if --dump-outputs is given (dump_outputs below), print ONE JSON line on rank 0 with
+the headline value and `ms_per_step`.
+
+With --full the same K-step window is also timed once before, after only the W warm-up steps (the
+GPU from idle: `value_without_settle`), the first frame is checked against the oracle, and the line
+also carries (rank 0, N = 1; --no-extras and --no-cpu-baseline leave parts of it out):
   roofline      k_score, the inlier-scoring kernel: algorithmic bytes (12 B per point of every
                 (active frame, tile) a launch reads) / its average launch time, HIP events on its
                 stream over a pass with one batch in flight
@@ -371,6 +376,46 @@ def streaming_pass(pitt, ctxs, batches, dev, threads, params, steps, clutter_per
             "note": "a step = a device-to-device copy of new frames into the context's buffers, then its batch"}
 
 
+DUMP_SAMPLE_FRAMES = 16  # whole inlier lists written: 16 x 307,200 x 4 B = 19.7 MB at most
+
+
+def dump_outputs(path, recs, frame_start, local):
+    """--dump-outputs: what a caller of the timed path received from its last timed step, as float
+    arrays (the frames are generated from fixed seeds, so two builds can be compared file by file).
+      <field>.npy             one file per field of the per-frame result records `recs` (gathered over
+                              the ranks when N > 1): coefficients float32 [F, 4], the integer fields
+                              float64 [F] (exact)
+      inlier_index_sums.npy   float64 [L]: the sum of every local frame's final inlier indices (exact:
+                              below 2^53), so every frame's list is covered
+      inlier_sample_frames.npy, inlier_sample.npy
+                              a fixed seeded sample of at most DUMP_SAMPLE_FRAMES local frames (their
+                              indices in `recs`, float64) and their whole ascending inlier lists,
+                              float32 [S, max length] (indices < 2^24: exact), padded with -1
+    `local`: this rank's (batch, inlier tensor) pairs of that step in frame order, frame_start its
+    first frame's index in `recs`; the inlier files are left out when the run wrote no inlier lists."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name in recs.dtype.names:
+        a = recs[name]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+    if any(out is None for _, out in local):
+        return
+    where = [(b, out, f) for b, out in local for f in range(b.n_frames)]  # local frame -> its batch
+    n_inl = recs["n_inliers"][frame_start:frame_start + len(where)]
+    sums = torch.stack([out[int(b.offsets[f]):int(b.offsets[f]) + int(n)].sum(dtype=torch.int64)
+                        for (b, out, f), n in zip(where, n_inl)])
+    np.save(os.path.join(path, "inlier_index_sums.npy"), sums.cpu().numpy().astype(np.float64))
+    pick = np.sort(np.random.default_rng(20240607).choice(len(where), min(DUMP_SAMPLE_FRAMES, len(where)),
+                                                           replace=False))
+    sample = np.full((len(pick), max(1, int(n_inl[pick].max()))), -1.0, np.float32)
+    for row, k in enumerate(pick):
+        b, out, f = where[k]
+        o = int(b.offsets[f])
+        sample[row, :int(n_inl[k])] = out[o:o + int(n_inl[k])].cpu().numpy()
+    np.save(os.path.join(path, "inlier_sample_frames.npy"), (pick + frame_start).astype(np.float64))
+    np.save(os.path.join(path, "inlier_sample.npy"), sample)
+
+
 ORIG_HW_QUEUES = None  # the caller's GPU_MAX_HW_QUEUES, before main() raises it for the pipelined pass
 
 
@@ -634,9 +679,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames-per-gpu", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the no-settle window, the oracle spot check, the roofline "
+                         "pass, the extra passes and the CPU baseline (a plain run only times the K steps)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the outputs of the last timed step to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the clutter / PCIe / config-5 passes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the clutter / PCIe / config-5 passes")
     ap.add_argument("--no-inliers", action="store_true", help="skip writing the final inlier lists")
     # 4 batches in flight, each context's stream on its own hardware queue (profiles/r03p_*: 370.8k
     # frames/s against 355.2k at 3 in flight on the box's default 4 queues; 4 in flight sharing 4
@@ -793,10 +844,10 @@ def main():
     for i in range(len(ctxs)):
         for _ in range(2):
             ctxs[i].plane_segment_batch(batches[i], params, outs[i])
-    # parity spot check outside the timed region (first frame of this rank vs the oracle), before the
-    # warm-up steps: the oracle's CPU time leaves the GPU idle, and the timed region should start on
+    # --full: parity spot check outside the timed region (first frame of this rank vs the oracle), before
+    # the warm-up steps: the oracle's CPU time leaves the GPU idle, and the timed region should start on
     # the clocks the warm-up steps brought up, not on an idle GPU's
-    if rank == 0:
+    if rank == 0 and args.full:
         res0 = ctx.plane_segment_batch(batches[0], params, outs[0])
         o = oracle().plane_segment(*frames0[0])
         ok = (np.array_equal(res0[0]["coefficients"], o.coefficients) and res0[0]["n_inliers"] == len(o.inliers)
@@ -825,13 +876,15 @@ def main():
             d = float(t.item())
         return d, r
 
-    # ---- the same K-step window with only the W warm-up steps before it (no settle steps): the GPU
-    # comes from the setup's serial batches and the oracle's CPU time, as a bench without settling
+    # ---- --full: the same K-step window with only the W warm-up steps before it (no settle steps): the
+    # GPU comes from the setup's serial batches and the oracle's CPU time, as a bench without settling
     # would time it.  Reported beside `value` as `value_without_settle`, never instead of it. ----
-    for _ in range(args.warmup):
-        timed_step()
-    timed_drain()
-    dt_cold, _ = timed_window(args.steps)
+    dt_cold = None
+    if args.full:
+        for _ in range(args.warmup):
+            timed_step()
+        timed_drain()
+        dt_cold, _ = timed_window(args.steps)
     # settle, then warm up: --settle-steps pipelined untimed steps before the W warm-up steps.  After
     # the setup's serial batches and the oracle's CPU time the GPU has been idle or lightly loaded, and
     # the first tens of milliseconds of pipelined work run slower per step (clocks and power settling):
@@ -849,10 +902,19 @@ def main():
         gather.seconds, gather.posted = 0.0, 0
     dt, res = timed_window(args.steps)
     rec_dump = None if records[0] is None else records[0].copy()  # before the extra passes reuse the slots
-    # the same pipelined step over 200 timed steps right after the headline's (1 GPU, default extras, when
-    # fewer steps were asked): the steady state beside the short window's fill and drain; never `value`
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's slot: its records (`res`) and the inlier lists still in its tensors
+        if parts > 1:
+            j = (pcounter[0] - 1) % args.pipeline
+            last = [(pbatches[k], pouts[k]) for k in range(j * parts, (j + 1) * parts)]
+        else:
+            j = (counter[0] - 1) % len(ctxs)
+            last = [(batches[j], outs[j])]
+        dump_outputs(args.dump_outputs, res, start, last)
+    # --full: the same pipelined step over 200 timed steps right after the headline's (1 GPU, default extras,
+    # when fewer steps were asked): the steady state beside the short window's fill and drain; never `value`
     steady = None
-    if world == 1 and not args.no_extras and args.steps < 200:
+    if args.full and world == 1 and not args.no_extras and args.steps < 200:
         torch.cuda.synchronize()
         ts = time.perf_counter()
         for _ in range(200):
@@ -865,33 +927,32 @@ def main():
                           "amortised); reported beside `value`, not instead of it"}
         log(f"[rank 0] steady state: {steady}")
 
-    # ---- roofline pass: one batch at a time, HIP events around every launch on the launch stream
+    # ---- --full: roofline pass: one batch at a time, HIP events around every launch on the launch stream
     # (a concurrent batch would share HBM and stretch the kernel's duration) ----
-    roof_steps = max(1, min(args.steps, 10))
-    # every batch layout once on this context first (unprofiled): the adaptive chunk schedule learns per
-    # layout, and a layout's first batch launches every chunk
-    for k in range(len(batches)):
-        ctx.plane_segment_batch(batches[k], params, outs[k])
-    ctx.profile(True)
-    ctx.profile_reset()
-    for k in range(roof_steps):
-        ctx.plane_segment_batch(batches[k % len(batches)], params, outs[k % len(batches)])
-    launches, ms, nbytes = ctx.profile_get("k_score")
-    n_empty, ms_empty, _ = ctx.profile_get("k_score:empty")
-    kernels = kernel_table(ctx, roof_steps)
-    if rank == 0:
-        for k, v in kernels.items():
-            log(f"[rank 0] {k:15s} launches/batch {v['launches_per_batch']:5.1f}  {v['us_per_batch']:8.1f} us/batch  "
-                f"avg {v['avg_launch_us']:8.1f} us  {v['GBps']:8.1f} GB/s")
-    ctx.profile(False)
+    if args.full:
+        roof_steps = max(1, min(args.steps, 10))
+        # every batch layout once on this context first (unprofiled): the adaptive chunk schedule learns per
+        # layout, and a layout's first batch launches every chunk
+        for k in range(len(batches)):
+            ctx.plane_segment_batch(batches[k], params, outs[k])
+        ctx.profile(True)
+        ctx.profile_reset()
+        for k in range(roof_steps):
+            ctx.plane_segment_batch(batches[k % len(batches)], params, outs[k % len(batches)])
+        launches, ms, nbytes = ctx.profile_get("k_score")
+        n_empty, ms_empty, _ = ctx.profile_get("k_score:empty")
+        kernels = kernel_table(ctx, roof_steps)
+        if rank == 0:
+            for k, v in kernels.items():
+                log(f"[rank 0] {k:15s} launches/batch {v['launches_per_batch']:5.1f}  {v['us_per_batch']:8.1f} us/batch  "
+                    f"avg {v['avg_launch_us']:8.1f} us  {v['GBps']:8.1f} GB/s")
+        ctx.profile(False)
     hyps = res["hypotheses"]
 
     line = None
     if rank == 0:
         lib_sha = library_sha16()
-        traffic, traffic_note = pmc_traffic(lib_sha)
-        avg_ms = ms / max(1, launches)
-        achieved = (nbytes / max(1, launches)) / (avg_ms * 1e-3) / 1e9 if launches else 0.0
+        cold_steps = args.warmup + args.steps if args.full else 0  # the no-settle window and its warm-up steps
         line = {
             "metric": METRIC,
             "value": round(total * args.steps / dt, 2),
@@ -899,10 +960,9 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            # every pipelined step run before the timed K (untimed): the W warm-up steps before the
-            # no-settle window, that window's K steps, the settle steps and the W warm-up steps again
-            "untimed_steps": 2 * args.warmup + args.steps + args.settle_steps,
-            "value_without_settle": round(total * args.steps / dt_cold, 2),
+            # every pipelined step run before the timed K (untimed): the settle steps and the W warm-up
+            # steps; with --full, before them, the W warm-up steps and the K steps of the no-settle window
+            "untimed_steps": cold_steps + args.settle_steps + args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -918,11 +978,12 @@ def main():
                 "points_per_frame": W * H,
                 "parallelism": f"frame-sharded x{world}, {args.pipeline} batches in flight per GPU"
                                + (f", each split over {parts} contexts" if parts > 1 else ""),
-                "untimed_before_timed": {"warmup_steps": args.warmup, "no_settle_window_steps": args.steps,
-                                         "settle_steps": args.settle_steps, "warmup_steps_again": args.warmup,
-                                         "note": "value_without_settle = the same K-step window timed after only "
-                                                 "the W warm-up steps (the GPU from idle); value = the K-step "
-                                                 "window after the settle steps"},
+                "untimed_before_timed": ({"warmup_steps": args.warmup, "no_settle_window_steps": args.steps,
+                                          "settle_steps": args.settle_steps, "warmup_steps_again": args.warmup,
+                                          "note": "value_without_settle = the same K-step window timed after only "
+                                                  "the W warm-up steps (the GPU from idle); value = the K-step "
+                                                  "window after the settle steps"} if args.full else
+                                         {"settle_steps": args.settle_steps, "warmup_steps": args.warmup}),
                 "hypotheses_per_frame_mean": round(float(np.mean(hyps)), 2),
                 "world_size_seen": world,
                 "collective": (f"{backend} all_gather_into_tensor of per-frame records, async (collected one "
@@ -932,30 +993,35 @@ def main():
                 # runtime knobs of the exact kernel variants (read when a context is created)
                 "knobs": {k: os.environ[k] for k in sorted(os.environ) if k.startswith("PITT_")} or None,
             },
-            "roofline": {
-                "kernel": "k_score",
-                "bound": "hbm",
-                "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": traffic,
-                "traffic_source": traffic_note,
-                "launches": launches,
-                "measured": f"HIP events on k_score's stream over a separate {roof_steps}-batch pass with one "
-                            "batch in flight (the timed pass overlaps batches on several streams); launches "
-                            "that score at least one tile (chunks with no active frame are listed apart)",
-                "empty_launches": n_empty,
-                "empty_us_per_batch": round(ms_empty / roof_steps * 1e3, 1),
-                "avg_launch_us": round(avg_ms * 1e3, 2),
-                "algorithmic_bytes_per_launch": round(nbytes / max(1, launches), 1),
-            },
-            "kernels": kernels,
             "library_sha16": lib_sha,
         }
+    if rank == 0 and args.full:
+        traffic, traffic_note = pmc_traffic(lib_sha)
+        avg_ms = ms / max(1, launches)
+        achieved = (nbytes / max(1, launches)) / (avg_ms * 1e-3) / 1e9 if launches else 0.0
+        line["value_without_settle"] = round(total * args.steps / dt_cold, 2)
+        line["roofline"] = {
+            "kernel": "k_score",
+            "bound": "hbm",
+            "achieved": round(achieved, 1),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": traffic,
+            "traffic_source": traffic_note,
+            "launches": launches,
+            "measured": f"HIP events on k_score's stream over a separate {roof_steps}-batch pass with one "
+                        "batch in flight (the timed pass overlaps batches on several streams); launches "
+                        "that score at least one tile (chunks with no active frame are listed apart)",
+            "empty_launches": n_empty,
+            "empty_us_per_batch": round(ms_empty / roof_steps * 1e3, 1),
+            "avg_launch_us": round(avg_ms * 1e3, 2),
+            "algorithmic_bytes_per_launch": round(nbytes / max(1, launches), 1),
+        }
+        line["kernels"] = kernels
         if steady is not None:
             line["steady_state"] = steady
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         line["cov_fast"] = cov_fast_pass(pitt, ctx, batches, outs, params, step, drain, args.steps, B)
         log(f"[rank 0] cov_fast: {line['cov_fast']}")
         clutter_frames, line["clutter"] = clutter_pass(pitt, ctx, dev, threads)
@@ -974,7 +1040,7 @@ def main():
         log(f"[rank 0] classify: {line['classify']}")
     else:
         clutter_frames = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cl = clutter_frames[0] if clutter_frames else make_frames([0], 1, pitt.SCENE_CLUTTER)[0]
         line["cpu_baseline"] = cpu_baseline(frames0, cl, cpus, args.cpu_budget)
     if rank == 0 and args.dump_records:

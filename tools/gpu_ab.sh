@@ -7,7 +7,7 @@
 # first scoring chunk's average launch.  Every GPU step has its own time limit; the script stops
 # at the first failure.
 set -o pipefail
-TESTS=""; ROUNDS=2; BARGS="--no-extras --no-cpu-baseline"
+TESTS=""; ROUNDS=2; BARGS="--full --no-extras --no-cpu-baseline"
 while getopts "t:r:b:" o; do case $o in t) TESTS=$OPTARG;; r) ROUNDS=$OPTARG;; b) BARGS=$OPTARG;; *) exit 2;; esac; done
 shift $((OPTIND - 1))
 mkdir -p gpurun_out

@@ -14,6 +14,6 @@ mkdir -p "$OUT"
 i=0
 for set in "$@"; do
     timeout -k 10 120 rocprofv3 --pmc $set --kernel-include-regex "$KRE" -d "$OUT/pmc_${TAG}_$i" -o p -f csv -- \
-        python3 "$ROOTDIR/bench.py" --steps 2 --warmup 1 --pipeline 1 --no-cpu-baseline > "$OUT/pmc_${TAG}_$i.log" 2>&1 || exit $?
+        python3 "$ROOTDIR/bench.py" --steps 2 --warmup 1 --pipeline 1 --full --no-cpu-baseline > "$OUT/pmc_${TAG}_$i.log" 2>&1 || exit $?
     i=$((i + 1))
 done

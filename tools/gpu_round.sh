@@ -16,6 +16,6 @@ if grep -qiE "illegal memory access|memory access fault|hipErrorIllegalAddress|H
     echo "GPU fault in the test run: stopping"; exit 3
 fi
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 400 python -u bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.log || { tail -30 $OUT/${TAG}_bench.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.log || { tail -30 $OUT/${TAG}_bench.log; exit 1; }
 python -c "import json,sys; d=json.load(open('$OUT/${TAG}_bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d.get('config5',{}).get('gpu_ms_per_scene'), d.get('classify',{}).get('ms_per_frame'))"
 exit $rc

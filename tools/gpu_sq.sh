@@ -10,7 +10,7 @@ shift 2
 cd /tmp && export TMPDIR=/tmp
 OUT="$ROOTDIR/gpurun_out"
 mkdir -p "$OUT"
-BENCH="$ROOTDIR/bench.py --steps 2 --warmup 1 --pipeline 1 --no-cpu-baseline $*"
+BENCH="$ROOTDIR/bench.py --steps 2 --warmup 1 --pipeline 1 --full --no-cpu-baseline $*"
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU \
     SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS --kernel-include-regex "$KRE" \
     -d "$OUT/sq_${TAG}_a" -o a -f csv -- python3 $BENCH > "$OUT/sq_${TAG}_a.log" 2>&1 || exit $?
