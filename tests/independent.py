@@ -10,6 +10,10 @@ covariance, float64 eigen-solves, and scipy graph components for Euclidean clust
                               sequential in inlier order (np.cumsum is sequential), accu *= 1/n (A9)
   plane_expectations(...)     eig64 / lsq64 planes and their tolerances (tools/make_independent_golden.py)
   cluster_labels(...)         cKDTree.query_pairs + connected_components, clusterize's size filter
+  radius_components(...)      the radius graph by the dense float32 distance matrix in FLANN's operation
+                              order ((ex ex + ey ey) + ez ez < r^2), connected_components
+  brute_knn(...)              exhaustive k nearest neighbours ordered by (float32 distance, index)
+  seq_sum32(v)                one sequential float32 sum
 """
 import numpy as np
 
@@ -98,6 +102,60 @@ def cluster_labels(x, y, z, radius=0.03, min_rate=0.01, max_rate=0.99):
     for rank, c in enumerate(kept):
         lab[comp == c] = rank
     return lab
+
+
+def radius2(tol):
+    """KdTreeFLANN::radiusSearch's squared radius: (float)((double)(float)tol * (float)tol)."""
+    return np.float32(np.float64(np.float32(tol)) ** 2)
+
+
+def pair_dd32(x, y, z, rows):
+    """FLANN L2_Simple between points `rows` and every point: (ex ex + ey ey) + ez ez in float32."""
+    ex, ey, ez = (v[rows, None] - v[None, :] for v in (x, y, z))
+    return (ex * ex + ey * ey) + ez * ez
+
+
+def radius_components(x, y, z, tol, block=512):
+    """Components of the graph with an edge where the float32 FLANN distance is < radius2(tol), by the
+    dense O(n^2) distance matrix (n up to about 6000); a point with a non-finite coordinate is a
+    singleton.  Returns (per-point component label, the components as ascending index tuples)."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    x, y, z = (np.ascontiguousarray(v, np.float32) for v in (x, y, z))
+    n, r2 = len(x), radius2(tol)
+    fin = np.isfinite(x) & np.isfinite(y) & np.isfinite(z)
+    ii, jj = [], []
+    with np.errstate(invalid="ignore", over="ignore"):
+        for b in range(0, n, block):
+            rows = np.arange(b, min(b + block, n))
+            i, j = np.nonzero((pair_dd32(x, y, z, rows) < r2) & fin[rows, None] & fin[None, :])
+            ii.append(i + b)
+            jj.append(j)
+    ii, jj = np.concatenate(ii), np.concatenate(jj)
+    g = coo_matrix((np.ones(len(ii), np.int8), (ii, jj)), shape=(n, n))
+    _, lab = connected_components(g, directed=False)
+    order = np.argsort(lab, kind="stable")
+    cuts = np.nonzero(np.diff(lab[order]))[0] + 1
+    return lab, [tuple(int(i) for i in c) for c in np.split(order, cuts)]
+
+
+def brute_knn(x, y, z, k):
+    """Per finite query its k nearest finite points (itself included, fewer when there are fewer),
+    ordered by (float32 FLANN distance of d = q - p, index); a non-finite query gets an empty list."""
+    x, y, z = (np.ascontiguousarray(v, np.float32) for v in (x, y, z))
+    fin = np.nonzero(np.isfinite(x) & np.isfinite(y) & np.isfinite(z))[0]
+    fx, fy, fz = x[fin], y[fin], z[fin]
+    out = [np.zeros(0, np.int64)] * len(x)
+    for q in fin:
+        dx, dy, dz = x[q] - fx, y[q] - fy, z[q] - fz
+        d = (dx * dx + dy * dy) + dz * dz
+        out[q] = fin[np.lexsort((fin, d))[:k]]
+    return out
+
+
+def seq_sum32(v):
+    """The sequential float32 chain ((v0 + v1) + v2) + ... (np.cumsum does not reassociate)."""
+    return np.cumsum(np.asarray(v, np.float32), dtype=np.float32)[-1]
 
 
 def labels_from_clusters(n, clusters):

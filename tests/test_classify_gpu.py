@@ -6,6 +6,9 @@ entry point runs all clusters through every stage together; each stage runs the 
 kernels on the same values, so its counts, coefficients, heights, centroids and tags must equal the
 per-cluster services' (pitt_srv_ransac_*, themselves held to the oracle in test_services_gpu.py) bit for
 bit."""
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -108,6 +111,29 @@ def test_batch_equals_per_cluster_services(ctx, srv):
     for a, b in zip(got, got2):
         assert a["inliers"] == b["inliers"] and a["tag"] == b["tag"]
         assert all(np.array_equal(_bits(x), _bits(y)) for x, y in zip(a["coefficients"], b["coefficients"]))
+
+
+# normals.hip: `constexpr int64_t kSegBrute = 16384;` -- k_knn_seg searches a cluster of up to kSegBrute
+# points exhaustively; a larger one goes through normals_impl (the grid path) on its own.
+K_SEG_BRUTE = 16384
+
+
+def test_clusters_at_the_brute_force_limit(ctx, srv):
+    """A frame whose clusters have kSegBrute and kSegBrute + 1 points (the last exhaustive search and the
+    first hand-over to normals_impl) beside two small ones: all four as the per-cluster services."""
+    import torch
+    src = os.path.join(os.path.dirname(pitt.__file__), "csrc", "normals.hip")
+    with open(src) as f:
+        m = re.search(r"constexpr int64_t kSegBrute = (\d+);", f.read())
+    assert m and int(m.group(1)) == K_SEG_BRUTE, "kSegBrute changed: move this test's cluster sizes with it"
+    rng = np.random.default_rng(7)
+    cl = [sphere_scene(300, 40, 71, radius=0.03), cylinder_scene(K_SEG_BRUTE - 1000, 1000, 72)[0],
+          cylinder_scene(K_SEG_BRUTE - 999, 1000, 73, r=0.05)[0], _box(400, 74)]
+    clusters = [np.ascontiguousarray(c.astype(np.float32)[rng.permutation(len(c))]) for c in cl]
+    assert [len(c) for c in clusters] == [340, K_SEG_BRUTE, K_SEG_BRUTE + 1, 400]
+    xyz, offs, cnt = _layout(clusters)
+    d = [torch.from_numpy(np.ascontiguousarray(xyz[:, k])).cuda() for k in range(3)]
+    _check_against_services(ctx, srv, clusters, srv.classify_clusters(*d, offs, cnt))
 
 
 def test_host_memory_and_repeated_calls(ctx, srv):
