@@ -14,10 +14,19 @@ covariance, float64 eigen-solves, and scipy graph components for Euclidean clust
                               order ((ex ex + ey ey) + ez ez < r^2), connected_components
   brute_knn(...)              exhaustive k nearest neighbours ordered by (float32 distance, index)
   seq_sum32(v)                one sequential float32 sum
+  sphere_select32(P, c, t)    SampleConsensusModelSphere::selectWithinDistance in numpy float32, bit-exact:
+                              |sqrt((dx dx + dy dy) + dz dz) - r| < float32(t)
+  cylinder_distance64(...)    SampleConsensusModelCylinder / Cone::getDistancesToModel in plain float64 (the
+  cone_distance64(...)        distance to the surface and the folded normal angle, weighted); not the float
+                              operation order, so results are compared through band_check
+  band_check(d, th, inl, b)   the points an inlier list must have (d < th - b) and must not have (d > th + b)
+  lm_residuals64(model, P)    the OptimizationFunctor residuals of the three primitives in float64
+  lm_cost64(model, P, inl, c) their sum of squares over an inlier list
 """
 import numpy as np
 
 TH = 0.007
+MODEL_SPHERE, MODEL_CYLINDER, MODEL_CONE = 0, 1, 2
 
 
 def select(x, y, z, c, th=TH):
@@ -163,3 +172,96 @@ def labels_from_clusters(n, clusters):
     for rank, idx in enumerate(clusters):
         lab[np.asarray(idx)] = rank
     return lab
+
+
+# ---- the primitive services (test_primitive_edges.py) ----------------------------------------------
+def sphere_select32(P, coef, t):
+    """sac_model_sphere.hpp selectWithinDistance in float32: the centre subtracted per axis, the three
+    squares summed left to right, sqrt, minus the radius, abs, compared with the float threshold."""
+    P = np.asarray(P, np.float32)
+    c = np.asarray(coef, np.float32)
+    dx, dy, dz = P[:, 0] - c[0], P[:, 1] - c[1], P[:, 2] - c[2]
+    with np.errstate(invalid="ignore"):
+        d = np.abs(np.sqrt((dx * dx + dy * dy) + dz * dz) - c[3])
+        return np.nonzero(d < np.float32(t))[0].astype(np.int32)
+
+
+def _unit64(v):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def _folded_angle64(a, b):
+    """The angle between unit vectors, folded to [0, pi / 2] (getAngle3D, then min(a, pi - a))."""
+    ang = np.arccos(np.clip((a * b).sum(-1), -1.0, 1.0))
+    return np.minimum(ang, np.pi - ang)
+
+
+def _axis_frame64(P, N, coef):
+    """A point's foot on the axis line (coef[:3], coef[3:6]), its distance to the line, the unit radial
+    direction and its unit normal, all float64."""
+    c = np.asarray(coef, np.float64)
+    p, n = np.asarray(P, np.float64), np.asarray(N, np.float64)
+    u = c[3:6] / np.linalg.norm(c[3:6])
+    v = p - c[:3]
+    foot = c[:3] + (v @ u)[:, None] * u
+    rad = p - foot
+    return c, foot, np.linalg.norm(rad, axis=1), _unit64(rad), _unit64(n)
+
+
+def cylinder_distance64(P, N, coef, w):
+    """|w a + (1 - w) | |p - axis| - r | |: a the folded angle between the point's normal and the radial
+    direction (sac_model_cylinder.hpp getDistancesToModel)."""
+    c, _, dist, radial, n = _axis_frame64(P, N, coef)
+    return np.abs(w * _folded_angle64(n, radial) + (1.0 - w) * np.abs(dist - c[6]))
+
+
+def cone_distance64(P, N, coef, w):
+    """|w a + (1 - w) | |p - axis| - tan(angle) |apex - foot| | |: a the folded angle between the point's
+    normal and the cone's normal sin(angle) h + cos(angle) radial at the point's height, h the unit vector
+    from the foot to the apex (sac_model_cone.hpp getDistancesToModel)."""
+    c, foot, dist, radial, n = _axis_frame64(P, N, coef)
+    h = c[:3] - foot
+    hn = np.linalg.norm(h, axis=1)
+    cone_n = np.sin(c[6]) * _unit64(h) + np.cos(c[6]) * radial
+    return np.abs(w * _folded_angle64(n, _unit64(cone_n)) + (1.0 - w) * np.abs(dist - np.tan(c[6]) * hn))
+
+
+def band_check(dist64, th, inliers, band):
+    """(missing, extra, in_band): the points with dist64 < th - band that the inlier list lacks, the listed
+    points with dist64 > th + band, and how many points lie inside the band (they may go either way).  A
+    non-finite distance never counts as an inlier."""
+    d = np.asarray(dist64, np.float64)
+    listed = np.zeros(len(d), bool)
+    listed[np.asarray(inliers, np.int64)] = True
+    with np.errstate(invalid="ignore"):
+        must, must_not = d < th - band, ~(d <= th + band)
+    return np.nonzero(must & ~listed)[0], np.nonzero(must_not & listed)[0], int((~must & ~must_not).sum())
+
+
+def lm_residuals64(model, P):
+    """The OptimizationFunctor residuals of sac_model_{sphere,cylinder,cone}.h as a function of the
+    coefficients, over the points P, in float64 (the operation order of the oracle's double LM)."""
+    px, py, pz = (P[:, k].astype(np.float64) for k in range(3))
+
+    def f(q):
+        if model == MODEL_SPHERE:
+            dx, dy, dz = px - q[0], py - q[1], pz - q[2]
+            return np.sqrt((dx * dx + dy * dy) + dz * dz) - q[3]
+        su = (q[3] * q[3] + q[4] * q[4]) + q[5] * q[5]
+        vx, vy, vz = q[0] - px, q[1] - py, q[2] - pz
+        wx, wy, wz = q[4] * vz - q[5] * vy, q[5] * vx - q[3] * vz, q[3] * vy - q[4] * vx
+        d2 = ((wx * wx + wy * wy) + wz * wz) / su
+        if model == MODEL_CYLINDER:
+            return d2 - q[6] * q[6]
+        k = (((px - q[0]) * q[3] + (py - q[1]) * q[4]) + (pz - q[2]) * q[5]) / su
+        hx, hy, hz = k * q[3], k * q[4], k * q[5]
+        r = np.tan(q[6]) * np.sqrt((hx * hx + hy * hy) + hz * hz)
+        return d2 - r * r
+    return f
+
+
+def lm_cost64(model, P, inliers, coef):
+    """The float64 sum of squared residuals of `coef` over the points listed in `inliers`."""
+    r = lm_residuals64(model, np.asarray(P)[np.asarray(inliers, np.int64)])(np.asarray(coef, np.float64))
+    return float((r * r).sum())

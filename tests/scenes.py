@@ -21,6 +21,13 @@ decide the result:
   sum_blobs                                        cluster sizes around the sum kernels' block sizes
   pow2_lattice, pow2_plane, clump_and_sheet, far_points   exact ties at the k-th neighbour, more
                                                    candidates than the kNN buffer holds, isolated points
+
+and the scenes of test_primitive_edges.py (these call the oracle to check or to build themselves):
+
+  exact_sphere, exact_cylinder, exact_cone   m low-noise model points whose raw RANSAC inliers are exactly
+                                             the labelled points, clutter 1 m away, a model point first and last
+  shell_scene                                points placed at the raw model's threshold +- 2e-6 m (two passes)
+  octahedron_sphere                          an analytic sphere with probes at the threshold and 1, 2 ulp off it
 """
 import math
 
@@ -307,3 +314,212 @@ def far_points(seed=31):
     rng = np.random.default_rng(seed)
     p = rng.uniform(-0.2, 0.2, (500, 3))
     return _split(np.concatenate([p, [[5.0, 5.0, 5.0], [-4.0, 3.0, 9.0]]]))
+
+
+# ---- primitive edge scenes (test_primitive_edges.py) ----------------------------------------------
+def _frame(axis):
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    u = np.cross(a, [1.0, 0.0, 0.0])
+    u /= np.linalg.norm(u)
+    return a, u, np.cross(a, u)
+
+
+def _unit_rows(v):
+    return v / np.linalg.norm(v, axis=1)[:, None]
+
+
+def _shuffle_labelled(rng, model, clutter):
+    """One shuffle of the model rows and the clutter rows together; then a model row is swapped to index 0
+    and another to index n - 1 (the counting and selection kernels' first and last point).  Returns the
+    float32 rows and the boolean label of the model rows."""
+    m, n = len(model), len(model) + len(clutter)
+    perm = rng.permutation(n)
+    rows = np.concatenate([model, clutter])[perm]
+    label = perm < m
+    for end in ((0, n - 1) if m >= 2 else (0,)):
+        if not label[end]:
+            other = [i for i in np.nonzero(label)[0] if i not in (0, n - 1)][0]
+            rows[[end, other]] = rows[[other, end]]
+            label[[end, other]] = label[[other, end]]
+    return rows.astype(np.float32), label
+
+
+def _raw_is_label(res, label, what):
+    assert res["ok"] and np.array_equal(res["inliers"], np.nonzero(label)[0]), \
+        f"{what}: the oracle's raw inliers are not the {int(label.sum())} labelled points"
+
+
+SPHERE_CENTRE, SPHERE_RADIUS = (0.3, -0.2, 1.1), 0.05
+AXIS, CYL_BASE, CYL_RADIUS, CONE_APEX, CONE_HALF_DEG = (0.1, 0.2, 1.0), (0.3, -0.1, 0.9), 0.04, (0.3, -0.1, 1.1), 25.0
+CLUTTER_SHIFT = np.array([1.0, 0.0, 0.0])  # the clutter box lies 1 m from the model
+
+
+def _sphere_points(rng, m, noise):
+    d = _unit_rows(rng.normal(size=(m, 3)))
+    d[:, 2] = -np.abs(d[:, 2])  # the camera sees one hemisphere
+    return np.asarray(SPHERE_CENTRE) + SPHERE_RADIUS * d + rng.normal(0, noise, (m, 3))
+
+
+def _cylinder_points(rng, m, noise, h=0.15):
+    a, u, v = _frame(AXIS)
+    t, ph = rng.uniform(0, h, m), rng.uniform(0, 2 * np.pi, m)
+    radial = np.cos(ph)[:, None] * u + np.sin(ph)[:, None] * v
+    p = np.asarray(CYL_BASE) + t[:, None] * a + CYL_RADIUS * radial + rng.normal(0, noise, (m, 3))
+    return np.c_[p, _unit_rows(radial + rng.normal(0, 0.02, (m, 3)))]
+
+
+def _cone_points(rng, m, noise, h=0.15):
+    a, u, v = _frame(AXIS)
+    half = np.deg2rad(CONE_HALF_DEG)
+    t, ph = rng.uniform(0.03, h, m), rng.uniform(0, 2 * np.pi, m)
+    radial = np.cos(ph)[:, None] * u + np.sin(ph)[:, None] * v
+    p = np.asarray(CONE_APEX) + t[:, None] * a + (t * np.tan(half))[:, None] * radial + rng.normal(0, noise, (m, 3))
+    return np.c_[p, _unit_rows(np.cos(half) * radial - np.sin(half) * a + rng.normal(0, 0.01, (m, 3)))]
+
+
+def _clutter(rng, n_out, centre, half_side, normals):
+    o = np.asarray(centre) + rng.uniform(-half_side, half_side, (n_out, 3))
+    return np.c_[o, _unit_rows(rng.normal(size=(n_out, 3)))] if normals else o
+
+
+def exact_sphere(m, n_out, seed, noise=0.0005, check=True):
+    """m points of a sphere (radius 0.05, noise 0.5 mm) and n_out clutter points in a 0.4 m box 1 m away,
+    shuffled (_shuffle_labelled).  Returns (P, label); with check, asserts that the sphere service's raw
+    RANSAC inliers (the oracle, optimize off) are exactly the labelled points, so its refinement gets
+    exactly m residuals."""
+    rng = np.random.default_rng(seed)
+    P, label = _shuffle_labelled(rng, _sphere_points(rng, m, noise),
+                                 _clutter(rng, n_out, SPHERE_CENTRE + CLUTTER_SHIFT, 0.2, False))
+    if check:
+        import oracle_binding as orc
+        _raw_is_label(orc.sphere_segment(*P.T, orc.sphere_params(optimize=False)), label,
+                      f"exact_sphere({m}, {n_out}, {seed})")
+    return P, label
+
+
+def exact_cylinder(m, n_out, seed, noise=0.0003, check=True):
+    """As exact_sphere for the cylinder service (radius 0.04, noise 0.3 mm, normals within about 0.02 rad of
+    the radial direction): (P, N, label)."""
+    rng = np.random.default_rng(seed)
+    rows, label = _shuffle_labelled(rng, _cylinder_points(rng, m, noise),
+                                    _clutter(rng, n_out, CYL_BASE + CLUTTER_SHIFT, 0.2, True))
+    P, N = np.ascontiguousarray(rows[:, :3]), np.ascontiguousarray(rows[:, 3:])
+    if check:
+        import oracle_binding as orc
+        _raw_is_label(orc.cylinder_segment(P, N, orc.cylinder_params(optimize=False)), label,
+                      f"exact_cylinder({m}, {n_out}, {seed})")
+    return P, N, label
+
+
+def exact_cone(m, n_out, seed, noise=0.0002, check=True):
+    """As exact_sphere for the cone service (half opening angle 25 degrees, 0.03 to 0.15 m from the apex,
+    noise 0.2 mm, normals within about 0.01 rad of the surface normal): (P, N, label)."""
+    rng = np.random.default_rng(seed)
+    rows, label = _shuffle_labelled(rng, _cone_points(rng, m, noise),
+                                    _clutter(rng, n_out, CONE_APEX + CLUTTER_SHIFT, 0.2, True))
+    P, N = np.ascontiguousarray(rows[:, :3]), np.ascontiguousarray(rows[:, 3:])
+    if check:
+        import oracle_binding as orc
+        _raw_is_label(orc.cone_segment(P, N, orc.cone_params(optimize=False)), label, f"exact_cone({m}, {n_out}, {seed})")
+    return P, N, label
+
+
+def _far_placeholders(rng, k, normals):
+    far = np.array([5.0, 5.0, 5.0]) + rng.uniform(-0.5, 0.5, (k, 3))
+    return np.c_[far, _unit_rows(rng.normal(size=(k, 3)))] if normals else far
+
+
+def shell_scene(model, seed, n_model=3000, n_out=400, n_shell=400, delta=2e-6):
+    """A threshold-shell scene in two passes.  Pass 1: n_model model points, n_out clutter points around
+    the model and n_shell placeholders metres away, shuffled; the oracle's raw RANSAC (optimize off) gives
+    the model M.  Pass 2: the placeholders are overwritten with points whose float64 service distance to M
+    is th + d, d uniform in +-delta, half of them inside M's surface and half outside.  For the cylinder
+    and the cone their normals are M's surface normal turned by an angle a in [0.2, 0.6] rad, every other
+    one reversed (so the fold min(a, pi - a) decides it), and the offset from the surface is solved for
+    w a + (1 - w) offset = th + d.  (Normals exactly along M's normal put every placed point where the
+    reference's float dot product rounds to 1 - ulp and its acos jumps by 3.5e-4 rad: the oracle then
+    differs from the float64 rule by up to 2.3e-7 m, and a band of four times that holds a third of the
+    placed points.)  The sampler depends only on (n, seed): the caller asserts that the raw model of the
+    final cloud is M again.  Returns (P, N or None, M, the placeholder indices)."""
+    import oracle_binding as orc
+    rng = np.random.default_rng(seed)
+    normals = model != "sphere"
+    if model == "sphere":
+        pts, centre, seg, prm = _sphere_points(rng, n_model, 0.001), SPHERE_CENTRE, orc.sphere_segment, orc.sphere_params
+    elif model == "cylinder":
+        pts, centre, seg, prm = _cylinder_points(rng, n_model, 0.001), CYL_BASE, orc.cylinder_segment, orc.cylinder_params
+    else:
+        # the cone is moved to 0.1 m from the origin: at 1 m the reference's float rounding of a point's foot
+        # on the axis (6e-8 m) alone puts it 5.5e-8 m from the float64 rule, and four times that is a band
+        # that holds a tenth of the placed points
+        pts, centre, seg, prm = _cone_points(rng, n_model, 0.0005), np.array([0.0, 0.0, 0.1]), orc.cone_segment, \
+            orc.cone_params
+        pts[:, :3] += centre - CONE_APEX
+    rows = np.concatenate([pts, _clutter(rng, n_out, centre, 0.2, normals), _far_placeholders(rng, n_shell, normals)])
+    perm = rng.permutation(len(rows))
+    rows = rows[perm].astype(np.float32)
+    shell = np.nonzero(perm >= n_model + n_out)[0]
+    P, N = np.ascontiguousarray(rows[:, :3]), (np.ascontiguousarray(rows[:, 3:]) if normals else None)
+    p = prm(optimize=False)
+    raw = seg(*P.T, p) if model == "sphere" else seg(P, N, p)
+    assert raw["ok"]
+    M = raw["coef"].astype(np.float64)
+    side = np.where(np.arange(n_shell) % 2 == 0, 1.0, -1.0)
+    D = p.threshold + rng.uniform(-delta, delta, n_shell)
+    if model == "sphere":
+        P[shell] = (M[:3] + (M[3] + side * D)[:, None] * _unit_rows(rng.normal(size=(n_shell, 3)))).astype(np.float32)
+        return P, None, raw["coef"], shell
+    w = p.normal_distance_weight
+    u = M[3:6] / np.linalg.norm(M[3:6])
+    e = _unit_rows(np.cross(u, rng.normal(size=(n_shell, 3))))  # unit vectors across the axis
+    k = (P[raw["inliers"]].astype(np.float64) - M[:3]) @ u   # the inliers' positions along the axis
+    k = rng.choice(k, n_shell)
+    turn = rng.uniform(0.2, 0.6, n_shell)
+    offset = side * (D - w * turn) / (1.0 - w)
+    if model == "cylinder":
+        rho, surface_n = M[6] + offset, e
+    else:
+        assert 0.0 < M[6] < np.pi / 2
+        rho = np.tan(M[6]) * np.abs(k) + offset
+        surface_n = np.sin(M[6]) * (-np.sign(k))[:, None] * u + np.cos(M[6]) * e
+    assert (rho > 0).all()
+    nrm = np.cos(turn)[:, None] * surface_n + np.sin(turn)[:, None] * np.cross(u, e)  # u x e is across both
+    nrm[(np.arange(n_shell) // 2) % 2 == 1] *= -1.0
+    P[shell] = (M[:3] + k[:, None] * u + rho[:, None] * e).astype(np.float32)
+    N[shell] = nrm.astype(np.float32)
+    return P, N, raw["coef"], shell
+
+
+OCTA_R, OCTA_T = 0.0625, 2.0 ** -7
+
+
+def octahedron_sphere(k, seed):
+    """The six vertices (+-r, 0, 0), (0, +-r, 0), (0, 0, +-r), r = 1/16, k times each, and 60 axis probes at
+    |x| = r +- t + j ulp, j = -2 .. 2, t = 2^-7, shuffled.  Every valid 4-sample of the vertices gives the
+    sphere (0, 0, 0, r) exactly, coplanar and repeated samples have m11 = 0 and are skipped.  For a probe
+    sqrt(x x) = |x| and | |x| - r | = t -+ j ulp are exact in float32, so with threshold t the expected
+    inliers follow from the construction: the vertices, the outer probes with j < 0 and the inner ones with
+    j > 0; a probe at distance t exactly is out.  Returns (P, expected inlier mask)."""
+    rng = np.random.default_rng(seed)
+    r, t = np.float32(OCTA_R), np.float32(OCTA_T)
+    rows, inl = [], []
+    for axis in range(3):
+        for sign in (1.0, -1.0):
+            v = np.zeros(3, np.float32)
+            v[axis] = sign * r
+            rows += [v] * k
+            inl += [True] * k
+            for shell in (r + t, r - t):
+                for j in range(-2, 3):
+                    a = np.float32(shell)
+                    for _ in range(abs(j)):
+                        a = np.nextafter(a, np.float32(1.0 if j > 0 else 0.0))
+                    d = np.abs(a - r)  # exact: a and r are multiples of a's ulp, the difference has few bits
+                    assert np.float64(d) == abs(np.float64(a) - np.float64(r))
+                    v = np.zeros(3, np.float32)
+                    v[axis] = sign * a
+                    rows.append(v)
+                    inl.append(bool(d < t))
+    perm = rng.permutation(len(rows))
+    return np.stack(rows)[perm], np.array(inl)[perm]

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as orc
+from independent import lm_residuals64
 from test_cone import CONE_PCL_TOL, cone_scene, same_cone
 from test_cylinder import CYL_PCL_TOL, cylinder_scene, same_line
 from test_sphere import SPHERE_PCL_ATOL, sphere_scene
@@ -29,24 +30,10 @@ CONVERGED = (1, 2, 3)  # RelativeReductionTooSmall, RelativeErrorTooSmall, both
 
 
 def _resid(model, P):
-    """The double residuals orc_elm_fit64 uses, in the same operation order."""
-    px, py, pz = (P[:, k].astype(np.float64) for k in range(3))
-
-    def f(q):
-        if model == orc.MODEL_SPHERE:
-            dx, dy, dz = px - q[0], py - q[1], pz - q[2]
-            return np.sqrt((dx * dx + dy * dy) + dz * dz) - q[3]
-        su = (q[3] * q[3] + q[4] * q[4]) + q[5] * q[5]
-        vx, vy, vz = q[0] - px, q[1] - py, q[2] - pz
-        wx, wy, wz = q[4] * vz - q[5] * vy, q[5] * vx - q[3] * vz, q[3] * vy - q[4] * vx
-        d2 = ((wx * wx + wy * wy) + wz * wz) / su
-        if model == orc.MODEL_CYLINDER:
-            return d2 - q[6] * q[6]
-        k = (((px - q[0]) * q[3] + (py - q[1]) * q[4]) + (pz - q[2]) * q[5]) / su
-        hx, hy, hz = k * q[3], k * q[4], k * q[5]
-        r = np.tan(q[6]) * np.sqrt((hx * hx + hy * hy) + hz * hz)
-        return d2 - r * r
-    return f
+    """The double residuals orc_elm_fit64 uses, in the same operation order (independent.lm_residuals64;
+    the model numbers are the oracle's)."""
+    assert (orc.MODEL_SPHERE, orc.MODEL_CYLINDER, orc.MODEL_CONE) == (0, 1, 2)
+    return lm_residuals64(model, P)
 
 
 def _raw(model, case):
