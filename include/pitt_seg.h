@@ -18,6 +18,8 @@
  *        src/segmentation_services/deep_filter_srv.cpp:37-44
  *   pitt_transform_cloud          replaces  pcl::transformPointCloud(cloud, out, Matrix4f)
  *        src/obj_segmentation.cpp:248
+ *   pitt_crop_boxes               replaces  the four chained CropBox<PointXYZ>::filter calls of the arm filter
+ *        src/segmentation_services/arm_filter_srv.cpp:66-103, :134-140 (called at src/obj_segmentation.cpp:244)
  *   pitt_unpack_pointcloud2       replaces  fromROSMsg (PointCloud2 -> PointCloud<PointXYZ>)
  *        src/point_cloud_library/pc_manager.cpp:94-104
  *   pitt_voxel_grid               replaces  VoxelGrid<PointXYZ>::filter (PCManager::downSampling)
@@ -51,6 +53,9 @@ extern "C" {
  * 4: pitt_graph_stats removed (the plane pipeline launches directly; HIP graphs measured no gain);
  *    pitt_multi_* (frame-sharded plane batches over several devices from one host process);
  *    pitt_find_supports_aos, pitt_euclidean_clusters_aos (host AoS clouds uploaded as they lie).
+ *    Added since, without a version change (new symbols only, no struct of an existing call changed):
+ *    pitt_crop_box, pitt_crop_box_from_rpy, pitt_crop_boxes, pitt_crop_boxes_host (the arm filter's
+ *    chained CropBox).
  * Callers check pitt_abi_version() == PITT_ABI_VERSION when they load the library: the structs passed
  * by pointer are read in this ABI's layout. */
 #define PITT_ABI_VERSION 4
@@ -362,6 +367,50 @@ int pitt_deep_filter(pitt_ctx* ctx, const float* x, const float* y, const float*
  * copied unchanged.  Device SoA in and out (out may not alias in). */
 int pitt_transform_cloud(pitt_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
                          const float matrix[16], int32_t dense, float* out_x, float* out_y, float* out_z);
+
+/* pcl::CropBox<PointXYZ> (PCL 1.7 filters/impl/crop_box.hpp, applyFilter(std::vector<int>&)), applied
+ * n_boxes times in a row as the arm filter does (src/segmentation_services/arm_filter_srv.cpp:66-103,
+ * :134-140; called at src/obj_segmentation.cpp:244).  One record per box, holding what CropBox has
+ * computed before its point loop (assumption A12). */
+#define PITT_CROP_MAX_BOXES 8
+typedef struct {
+    float   min[3], max[3];      /* CropBox::setMin / setMax, xyz (w unused)                      */
+    float   translation[3];      /* CropBox::setTranslation                                       */
+    float   inv_rotation[9];     /* row-major linear part of PCL's inverse_transform              */
+    int32_t has_translation;     /* translation_ != Vector3f::Zero()                              */
+    int32_t has_rotation;        /* rotation_ != Zero() and !inverse_transform.matrix().isIdentity() */
+} pitt_crop_box;
+
+/* Host, no device needed: the record of a box with setMin(min), setMax(max), setTranslation(translation),
+ * setRotation(rpy) (roll, pitch, yaw) and the identity setTransform.  has_translation: any component
+ * != 0.  With rpy all == 0 there is no rotation; otherwise the float matrix of
+ * pcl::getTransformation(0, 0, 0, roll, pitch, yaw), Eigen's float 3x3 inverse of it (cofactors times
+ * 1 / det) in inv_rotation, and has_rotation = 0 when that inverse passes Eigen's fuzzy isIdentity()
+ * (precision 1e-5: PCL then skips the multiply).  Without a rotation inv_rotation is the identity. */
+int pitt_crop_box_from_rpy(const float min[3], const float max[3], const float translation[3],
+                           const float rpy[3], pitt_crop_box* out);
+
+/* Every point p (always the original coordinates) goes through the stages k = 0 .. n_boxes - 1 in order:
+ *   dense == 0 and a non-finite coordinate: the point fails (at stage 0);
+ *   l = p; has_translation: l -= translation; has_rotation: l.i = (r[3i] l.x + r[3i+1] l.y) + r[3i+2] l.z
+ *   (float, left to right, no FMA);
+ *   outside = l.x < min0 || l.y < min1 || l.z < min2 || l.x > max0 || l.y > max1 || l.z > max2 (faces are
+ *   inside; a NaN coordinate compares false: "inside");
+ *   the point passes the stage iff negative ? outside : !outside.
+ * A point is kept iff it passes every stage; kept points are written in input order, bits unchanged.
+ * removed[k] (host, n_boxes entries, optional) counts the points whose first failing stage is k: the
+ * reference's per-box "Removed points" numbers.  n_boxes == 0 has no stage: the cloud is copied, non-finite
+ * points included.  Device SoA in; device
+ * SoA out of capacity n (out may not alias in); boxes: host.  n_boxes outside [0, PITT_CROP_MAX_BOXES],
+ * a null output or an aliased output is PITT_E_INVALID before any device access. */
+int pitt_crop_boxes(pitt_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
+                    const pitt_crop_box* boxes, int32_t n_boxes, int32_t negative, int32_t dense,
+                    float* out_x, float* out_y, float* out_z, int64_t* n_out, int64_t* removed);
+/* The same on a host PointXYZ cloud (16-byte stride), uploaded as it lies; xyz16_out: host, capacity n
+ * points (may be xyz16 itself), each kept point's x, y, z with the pad set to 1.0f. */
+int pitt_crop_boxes_host(pitt_ctx* ctx, const float* xyz16, int64_t n, const pitt_crop_box* boxes,
+                         int32_t n_boxes, int32_t negative, int32_t dense, float* xyz16_out, int64_t* n_out,
+                         int64_t* removed);
 
 /* fromROSMsg(PointCloud2 -> PointCloud<PointXYZ>) as called by PCManager::cloudForRosMsg,
  * src/point_cloud_library/pc_manager.cpp:94-104: the XYZ fields of a device-

@@ -16,6 +16,7 @@
  *   pitt_srv_arbitrate        <-> clustersAcquisition's arbitration  ransac_segmentation.cpp:265-302
  *   pitt_srv_classify_clusters <-> clustersAcquisition's loop over a frame's clusters (normals, the four
  *                               services, the arbitration)            ransac_segmentation.cpp:230-302
+ *   pitt_srv_arm_filter / _dev <-> filter (four chained CropBox filters)  arm_filter_srv.cpp:112-179
  * Clouds are PCL PointXYZ arrays (x, y, z, pad: 16-byte stride), host memory.
  * Handler calls return 1 when the handler returns true, 0 when false, < 0 on an ABI error.
  */
@@ -131,6 +132,50 @@ int pitt_srv_segment_objects_dev(pitt_srv* srv, const float* x, const float* y, 
                                  pitt_scene* out);
 /* The two parameter sets pitt_srv_segment_objects_dev would use now (either pointer may be NULL). */
 int pitt_srv_resolved_params(pitt_srv* srv, pitt_support_params* sp, pitt_cluster_params* cp);
+
+/* --- the arm filter: filter(), src/segmentation_services/arm_filter_srv.cpp:112-179 ---------------
+ * The four request vectors (ArmFilter.srv); a vector whose length is not 3 selects the service default
+ * (getService3DArrayParameter, srv_manager.h:176-188; the defaults: arm_filter_srv.cpp:32-35). */
+typedef struct {
+    int32_t n_forearm_min;
+    float   forearm_min[8];   /* forearm_bounding_box_min_value */
+    int32_t n_forearm_max;
+    float   forearm_max[8];   /* forearm_bounding_box_max_value */
+    int32_t n_elbow_min;
+    float   elbow_min[8];     /* elbow_bounding_box_min_value   */
+    int32_t n_elbow_max;
+    float   elbow_max[8];     /* elbow_bounding_box_max_value   */
+} pitt_srv_arm_request;
+/* One camera -> arm frame StampedTransform as the service's TF loop leaves it (:236-247). */
+typedef struct {
+    double origin[3];         /* getOrigin()                */
+    double rotation[4];       /* getRotation(): x, y, z, w  */
+} pitt_srv_arm_pose;
+
+/* tf::Matrix3x3::setRotation(q) followed by getRPY(roll, pitch, yaw), in double (armFiltering :77-79).
+ * Host, no context needed.  q: x, y, z, w; rpy: roll, pitch, yaw. */
+int pitt_srv_quaternion_rpy(const double q[4], double rpy[3]);
+
+/* filter(): four chained CropBox filters with setNegative(true) -- poses[0..3] = left forearm, right
+ * forearm, left elbow, right elbow (:134-140), the forearm box for the first two and the elbow box for
+ * the last two; each box's translation and rotation are the pose's origin and roll / pitch / yaw cast to
+ * float (armFiltering :77-89).  dense = the input cloud's is_dense.  tf_error != 0: no filtering, the
+ * input cloud comes back unchanged and removed is all 0 (:148-152).
+ * used_out: the four used_* vectors in response order (forearm min, forearm max, elbow min, elbow max);
+ * removed: the per-box "Removed points" numbers of the service's log; boxes_out: the resolved records
+ * handed to pitt_crop_boxes (any of the three may be NULL).  Returns 1 (the handler returns true),
+ * < 0 on an error. */
+/* host PointXYZ cloud in and out (xyz16_out: capacity n; the pad of an output point is 1.0f) */
+int pitt_srv_arm_filter(pitt_srv* srv, const float* xyz16, int64_t n, int32_t dense,
+                        const pitt_srv_arm_request* req, const pitt_srv_arm_pose poses[4], int32_t tf_error,
+                        float* xyz16_out, int64_t* n_out, float used_out[12], int64_t removed[4],
+                        pitt_crop_box boxes_out[4]);
+/* device SoA in, device SoA out of capacity n (the HBM chain: between pitt_deep_filter and
+ * pitt_transform_cloud, obj_segmentation.cpp:241-248) */
+int pitt_srv_arm_filter_dev(pitt_srv* srv, const float* x, const float* y, const float* z, int64_t n, int32_t dense,
+                            const pitt_srv_arm_request* req, const pitt_srv_arm_pose poses[4], int32_t tf_error,
+                            float* out_x, float* out_y, float* out_z, int64_t* n_out, float used_out[12],
+                            int64_t removed[4], pitt_crop_box boxes_out[4]);
 
 #ifdef __cplusplus
 }

@@ -101,6 +101,24 @@ struct ClusterSegmentation {  // cluster_segmentation_srv.cpp:38-108
     } response;
 };
 
+struct ArmFilter {  // arm_filter_srv.cpp:112-179
+    struct Request {
+        PointCloud input_cloud;
+        bool is_dense = true;  // input_cloud.is_dense, as fromROSMsg hands it to the filters
+        std::vector<float> forearm_bounding_box_min_value;
+        std::vector<float> forearm_bounding_box_max_value;
+        std::vector<float> elbow_bounding_box_min_value;
+        std::vector<float> elbow_bounding_box_max_value;
+    } request;
+    struct Response {
+        PointCloud armless_cloud;
+        std::vector<float> used_forearm_bounding_box_min_value;
+        std::vector<float> used_forearm_bounding_box_max_value;
+        std::vector<float> used_elbow_bounding_box_min_value;
+        std::vector<float> used_elbow_bounding_box_max_value;
+    } response;
+};
+
 struct ClustersOutput {  // obj_segmentation.cpp:286-311
     std::vector<InliersCluster> cluster_objs;
 };
@@ -271,7 +289,34 @@ public:
     // pitt status.
     int segmentObjectsDev(const float* x, const float* y, const float* z, int64_t n, pitt_scene* out);
 
+    // arm_filter_srv.cpp: the state the service's TF loop keeps (:40-43, :236-253) -- the four camera ->
+    // arm frame transforms in filter()'s order (left forearm, right forearm, left elbow, right elbow)
+    // and the flag a failed lookup sets
+    struct StampedTransform {
+        double origin[3] = {0, 0, 0};       // getOrigin()
+        double rotation[4] = {0, 0, 0, 1};  // getRotation(): x, y, z, w
+    };
+    StampedTransform armTransforms[4];
+    bool tfError = false;
+    // tf::Matrix3x3::setRotation(q) then getRPY(roll, pitch, yaw), in double (armFiltering :77-79)
+    static void quaternionToRPY(const double q[4], double& roll, double& pitch, double& yaw);
+    // armFiltering's CropBox setup (:77-98): the pose's origin and roll / pitch / yaw cast to float
+    static pitt_crop_box armBox(const std::vector<float>& minValues, const std::vector<float>& maxValues,
+                                const StampedTransform& frame);
+    // arm_filter_srv.cpp:112-179 on a host cloud: the request's cloud in, response.armless_cloud out
+    bool filter(pitt_msgs::ArmFilter::Request& req, pitt_msgs::ArmFilter::Response& res);
+    // the same with the cloud as PointXYZ bytes (xyz16_out: capacity n) or in HBM (device SoA in, device
+    // SoA out of capacity n); the cloud fields of req / res are not touched.  removed (optional): the
+    // log's four "Removed points" numbers; boxes (optional): the four records handed to pitt_crop_boxes.
+    bool filter(const float* xyz16, size_t n, const pitt_msgs::ArmFilter::Request& req,
+                pitt_msgs::ArmFilter::Response& res, float* xyz16_out, int64_t* n_out, int64_t removed[4],
+                pitt_crop_box boxes[4]);
+    bool filterDev(const float* x, const float* y, const float* z, int64_t n, const pitt_msgs::ArmFilter::Request& req,
+                   pitt_msgs::ArmFilter::Response& res, float* ox, float* oy, float* oz, int64_t* n_out,
+                   int64_t removed[4], pitt_crop_box boxes[4]);
+
 private:
+    void armBoxes(const pitt_msgs::ArmFilter::Request& req, pitt_msgs::ArmFilter::Response& res, pitt_crop_box boxes[4]);
     static pitt_support_params resolveSupport(const pitt_msgs::SupportSegmentation::Request& req);
     pitt_msgs::SupportSegmentation::Request supportRequest();
 

@@ -210,6 +210,29 @@ class Scene(ctypes.Structure):
                 ("indices", ctypes.c_void_p)]
 
 
+PITT_CROP_MAX_BOXES = 8
+
+
+class CropBox(ctypes.Structure):
+    """pitt_crop_box (include/pitt_seg.h)."""
+    _fields_ = [("min", ctypes.c_float * 3), ("max", ctypes.c_float * 3), ("translation", ctypes.c_float * 3),
+                ("inv_rotation", ctypes.c_float * 9), ("has_translation", ctypes.c_int32),
+                ("has_rotation", ctypes.c_int32)]
+
+
+class SrvArmRequest(ctypes.Structure):
+    """pitt_srv_arm_request (include/pitt_srv.h)."""
+    _fields_ = [("n_forearm_min", ctypes.c_int32), ("forearm_min", ctypes.c_float * 8),
+                ("n_forearm_max", ctypes.c_int32), ("forearm_max", ctypes.c_float * 8),
+                ("n_elbow_min", ctypes.c_int32), ("elbow_min", ctypes.c_float * 8),
+                ("n_elbow_max", ctypes.c_int32), ("elbow_max", ctypes.c_float * 8)]
+
+
+class SrvArmPose(ctypes.Structure):
+    """pitt_srv_arm_pose (include/pitt_srv.h): origin, rotation quaternion (x, y, z, w)."""
+    _fields_ = [("origin", ctypes.c_double * 3), ("rotation", ctypes.c_double * 4)]
+
+
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
 _i64 = ctypes.c_int64
@@ -250,6 +273,11 @@ SIGNATURES = {
                                 _i64p, _f32p]),
     "pitt_transform_cloud": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32p, _i32, _vp, _vp, _vp]),
     "pitt_unpack_pointcloud2": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pitt_crop_box_from_rpy": (_i32, [_f32p, _f32p, _f32p, _f32p, ctypes.POINTER(CropBox)]),
+    "pitt_crop_boxes": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(CropBox), _i32, _i32, _i32, _vp, _vp, _vp,
+                               _i64p, _i64p]),
+    "pitt_crop_boxes_host": (_i32, [_vp, _f32p, _i64, ctypes.POINTER(CropBox), _i32, _i32, _i32, _f32p, _i64p,
+                                    _i64p]),
     "pitt_normal_estimation": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32p, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pitt_voxel_grid": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i32, _vp,
                                _vp, _vp, _i64p, _i32p]),
@@ -335,6 +363,12 @@ SIGNATURES.update({
     "pitt_srv_classify_clusters": (_i32, [_vp, _vp, _vp, _vp, _i64p, _i64p, _i32, ctypes.POINTER(ClusterShape)]),
     "pitt_srv_segment_objects_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(Scene)]),
     "pitt_srv_resolved_params": (_i32, [_vp, ctypes.POINTER(SupportParams), ctypes.POINTER(ClusterParams)]),
+    "pitt_srv_quaternion_rpy": (_i32, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "pitt_srv_arm_filter": (_i32, [_vp, _f32p, _i64, _i32, ctypes.POINTER(SrvArmRequest), ctypes.POINTER(SrvArmPose),
+                                   _i32, _f32p, _i64p, _f32p, _i64p, ctypes.POINTER(CropBox)]),
+    "pitt_srv_arm_filter_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, ctypes.POINTER(SrvArmRequest),
+                                       ctypes.POINTER(SrvArmPose), _i32, _vp, _vp, _vp, _i64p, _f32p, _i64p,
+                                       ctypes.POINTER(CropBox)]),
 })
 
 

@@ -73,6 +73,28 @@ def support_params(**kw) -> L.SupportParams:
     return p
 
 
+def crop_box(min, max, translation=(0.0, 0.0, 0.0), rpy=(0.0, 0.0, 0.0)) -> L.CropBox:
+    """The pitt_crop_box record of a pcl::CropBox with setMin / setMax / setTranslation / setRotation
+    (roll, pitch, yaw) and the identity transform (pitt_crop_box_from_rpy: host only)."""
+    v = [np.ascontiguousarray(np.asarray(a, np.float32).reshape(3)) for a in (min, max, translation, rpy)]
+    b = L.CropBox()
+    rc = lib.pitt_crop_box_from_rpy(*(_fp(a) for a in v), ctypes.byref(b))
+    if rc != L.PITT_OK:
+        raise PittError(rc, "pitt_crop_box_from_rpy")
+    return b
+
+
+def quaternion_rpy(q) -> np.ndarray:
+    """tf::Matrix3x3::setRotation(q).getRPY in double, as the arm filter mirror resolves a pose's
+    rotation: q = (x, y, z, w) -> float64 (roll, pitch, yaw).  Host only."""
+    qq = (ctypes.c_double * 4)(*[float(t) for t in q])
+    out = (ctypes.c_double * 3)()
+    rc = lib.pitt_srv_quaternion_rpy(qq, out)
+    if rc != L.PITT_OK:
+        raise PittError(rc, "pitt_srv_quaternion_rpy")
+    return np.array(list(out), np.float64)
+
+
 RESULT_DTYPE = np.dtype([("coefficients", np.float32, 4), ("n_coeff", np.int32), ("status", np.int32),
                          ("n_inliers", np.int64), ("hypotheses", np.int32), ("best_hypothesis", np.int32),
                          ("best_count", np.int64), ("rejected_samples", np.int32), ("flags", np.int32)])
@@ -311,6 +333,24 @@ class Context:
         cout = None if c is None else tuple(a[:nc.value] for a in c)
         fout = None if f is None else tuple(a[:nf.value] for a in f)
         return cout, fout, used.value
+
+    def crop_boxes(self, x, y, z, boxes, negative: bool = True, dense: bool = True):
+        """The arm filter's chained CropBox filters (arm_filter_srv.cpp:134-140) on device tensors:
+        `boxes` a sequence of pitt_crop_box records (crop_box()), applied in order.  Returns
+        ((x, y, z) of the kept points in input order, removed): removed[k] = points whose first failing
+        box is k."""
+        import torch
+        n = x.numel()
+        boxes = list(boxes)
+        arr = (L.CropBox * max(len(boxes), 1))(*boxes)
+        ox, oy, oz = (torch.empty(max(n, 1), dtype=torch.float32, device=x.device) for _ in range(3))
+        nout = ctypes.c_int64()
+        rem = np.zeros(max(len(boxes), 1), np.int64)
+        self._check(lib.pitt_crop_boxes(self.h, x.data_ptr(), y.data_ptr(), z.data_ptr(), n, arr, len(boxes),
+                                        1 if negative else 0, 1 if dense else 0, ox.data_ptr(), oy.data_ptr(),
+                                        oz.data_ptr(), ctypes.byref(nout), _i64(rem)), "pitt_crop_boxes")
+        k = nout.value
+        return (ox[:k], oy[:k], oz[:k]), rem[:len(boxes)]
 
     def transform_cloud(self, x, y, z, matrix, dense: bool = True):
         """pcl::transformPointCloud with a row-major 4x4 float matrix; device tensors in and out."""
@@ -868,6 +908,59 @@ class Services:
             lib.pitt_srv_cluster_get(self.h, k, _ip(idx), ctypes.byref(size), _fp(ce), _fp(cl))
             out.append(dict(inliers=idx[:size.value].copy(), centroid=ce, cloud=cl[:size.value, :3].copy()))
         return ok, out
+
+    @staticmethod
+    def _arm_args(poses, forearm_min, forearm_max, elbow_min, elbow_max):
+        r = L.SrvArmRequest()
+        for name, v in (("forearm_min", forearm_min), ("forearm_max", forearm_max), ("elbow_min", elbow_min),
+                        ("elbow_max", elbow_max)):
+            v = [float(t) for t in v][:8]
+            setattr(r, "n_" + name, len(v))
+            getattr(r, name)[:len(v)] = v
+        if len(poses) != 4:
+            raise ValueError("poses: left forearm, right forearm, left elbow, right elbow")
+        p = (L.SrvArmPose * 4)()
+        for k, (origin, quat) in enumerate(poses):
+            p[k].origin[:] = [float(t) for t in origin]
+            p[k].rotation[:] = [float(t) for t in quat]
+        return r, p
+
+    @staticmethod
+    def _arm_result(ok, used, rem, boxes):
+        return dict(ok=ok, used=used.reshape(4, 3), removed=rem, boxes=[boxes[k] for k in range(4)])
+
+    def arm_filter(self, cloud: np.ndarray, poses, forearm_min=(), forearm_max=(), elbow_min=(), elbow_max=(),
+                   dense: bool = True, tf_error: bool = False):
+        """filter() of the arm filter service (arm_filter_srv.cpp:112-179) on a host cloud.  poses: four
+        (origin[3], quaternion (x, y, z, w)) camera -> arm frame transforms: left forearm, right forearm,
+        left elbow, right elbow; a box vector whose length is not 3 selects the service default.
+        Returns (armless cloud (m, 4) PointXYZ, dict(ok, used (4, 3), removed[4], boxes[4]))."""
+        c = _cloud16(cloud)
+        n = c.shape[0]
+        r, p = self._arm_args(poses, forearm_min, forearm_max, elbow_min, elbow_max)
+        out = np.empty((max(n, 1), 4), np.float32)
+        m = ctypes.c_int64()
+        used, rem, boxes = np.zeros(12, np.float32), np.zeros(4, np.int64), (L.CropBox * 4)()
+        ok = self._rc(lib.pitt_srv_arm_filter(self.h, _fp(c), n, 1 if dense else 0, ctypes.byref(r), p,
+                                              1 if tf_error else 0, _fp(out), ctypes.byref(m), _fp(used), _i64(rem),
+                                              boxes), "arm_filter")
+        return out[:m.value].copy(), self._arm_result(ok, used, rem, boxes)
+
+    def arm_filter_dev(self, x, y, z, poses, forearm_min=(), forearm_max=(), elbow_min=(), elbow_max=(),
+                       dense: bool = True, tf_error: bool = False):
+        """arm_filter with the cloud in HBM (device tensors in and out): returns ((x, y, z), dict)."""
+        import torch
+        n = x.numel()
+        r, p = self._arm_args(poses, forearm_min, forearm_max, elbow_min, elbow_max)
+        ox, oy, oz = (torch.empty(max(n, 1), dtype=torch.float32, device=x.device) for _ in range(3))
+        m = ctypes.c_int64()
+        used, rem, boxes = np.zeros(12, np.float32), np.zeros(4, np.int64), (L.CropBox * 4)()
+        ok = self._rc(lib.pitt_srv_arm_filter_dev(self.h, x.data_ptr(), y.data_ptr(), z.data_ptr(), n,
+                                                  1 if dense else 0, ctypes.byref(r), p, 1 if tf_error else 0,
+                                                  ox.data_ptr(), oy.data_ptr(), oz.data_ptr(), ctypes.byref(m),
+                                                  _fp(used), _i64(rem), boxes), "arm_filter_dev")
+        k = m.value
+        return (ox[:k], oy[:k], oz[:k]), self._arm_result(ok, used, rem, boxes)
 
     def resolved_params(self):
         """(SupportParams, ClusterParams) that segment_objects_dev would use with the current parameters."""

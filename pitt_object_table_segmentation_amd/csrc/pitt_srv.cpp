@@ -561,6 +561,126 @@ std::vector<pitt_msgs::ClustersOutput> SegmentationServices::segmentObjects(cons
     return outs;
 }
 
+// ---- arm filter (arm_filter_srv.cpp) ----------------------------------------------------------
+namespace {
+// arm_filter_srv.cpp:32-35
+const float DEFAULT_PARAM_ARM_SRV_MIN_FOREARM_BOX[] = {-0.040f, -0.120f, -0.190f};
+const float DEFAULT_PARAM_ARM_SRV_MAX_FOREARM_BOX[] = {0.340f, 0.120f, 0.105f};
+const float DEFAULT_PARAM_ARM_SRV_MIN_ELBOW_BOX[] = {-0.090f, -0.135f, -0.160f};
+const float DEFAULT_PARAM_ARM_SRV_MAX_ELBOW_BOX[] = {0.440f, 0.135f, 0.110f};
+}  // namespace
+
+// tf LinearMath Matrix3x3.h: setRotation(q), then getRPY = getEulerYPR(yaw, pitch, roll), first solution
+void SegmentationServices::quaternionToRPY(const double q[4], double& roll, double& pitch, double& yaw) {
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    const double d = x * x + y * y + z * z + w * w;  // q.length2()
+    const double s = 2.0 / d;
+    const double xs = x * s, ys = y * s, zs = z * s;
+    const double wx = w * xs, wy = w * ys, wz = w * zs;
+    const double xx = x * xs, xy = x * ys, xz = x * zs;
+    const double yy = y * ys, yz = y * zs, zz = z * zs;
+    // rows m[0] = (1 - (yy + zz), xy - wz, xz + wy), m[1] = (xy + wz, 1 - (xx + zz), yz - wx),
+    // m[2] = (xz - wy, yz + wx, 1 - (xx + yy))
+    const double m0x = 1.0 - (yy + zz), m0y = xy - wz, m0z = xz + wy;
+    const double m1x = xy + wz;
+    const double m2x = xz - wy, m2y = yz + wx, m2z = 1.0 - (xx + yy);
+    const double kHalfPi = 1.57079632679489661923;  // TFSIMD_HALF_PI
+    if (std::fabs(m2x) >= 1.0) {  // gimbal lock: yaw = 0, the roll from the difference-of-angles formula
+        yaw = 0.0;
+        if (m2x < 0.0) {
+            pitch = kHalfPi;
+            roll = std::atan2(m0y, m0z);
+        } else {
+            pitch = -kHalfPi;
+            roll = std::atan2(-m0y, -m0z);
+        }
+    } else {
+        pitch = -std::asin(m2x);
+        roll = std::atan2(m2y / std::cos(pitch), m2z / std::cos(pitch));
+        yaw = std::atan2(m1x / std::cos(pitch), m0x / std::cos(pitch));
+    }
+}
+
+pitt_crop_box SegmentationServices::armBox(const std::vector<float>& minValues, const std::vector<float>& maxValues,
+                                           const StampedTransform& frame) {
+    double roll, pitch, yaw;
+    quaternionToRPY(frame.rotation, roll, pitch, yaw);
+    // Vector3f translation / rotation assigned from doubles (:82-89)
+    const float translation[3] = {(float)frame.origin[0], (float)frame.origin[1], (float)frame.origin[2]};
+    const float rotation[3] = {(float)roll, (float)pitch, (float)yaw};
+    pitt_crop_box b;
+    pitt_crop_box_from_rpy(minValues.data(), maxValues.data(), translation, rotation, &b);
+    return b;
+}
+
+void SegmentationServices::armBoxes(const pitt_msgs::ArmFilter::Request& req, pitt_msgs::ArmFilter::Response& res,
+                                    pitt_crop_box boxes[4]) {
+    // :117-120
+    const std::vector<float> minForearm =
+        srvm::getService3DArrayParameter(req.forearm_bounding_box_min_value, DEFAULT_PARAM_ARM_SRV_MIN_FOREARM_BOX);
+    const std::vector<float> maxForearm =
+        srvm::getService3DArrayParameter(req.forearm_bounding_box_max_value, DEFAULT_PARAM_ARM_SRV_MAX_FOREARM_BOX);
+    const std::vector<float> minElbow =
+        srvm::getService3DArrayParameter(req.elbow_bounding_box_min_value, DEFAULT_PARAM_ARM_SRV_MIN_ELBOW_BOX);
+    const std::vector<float> maxElbow =
+        srvm::getService3DArrayParameter(req.elbow_bounding_box_max_value, DEFAULT_PARAM_ARM_SRV_MAX_ELBOW_BOX);
+    // :134-140: left forearm, right forearm, left elbow, right elbow
+    boxes[0] = armBox(minForearm, maxForearm, armTransforms[0]);
+    boxes[1] = armBox(minForearm, maxForearm, armTransforms[1]);
+    boxes[2] = armBox(minElbow, maxElbow, armTransforms[2]);
+    boxes[3] = armBox(minElbow, maxElbow, armTransforms[3]);
+    // :173-176
+    res.used_forearm_bounding_box_min_value = minForearm;
+    res.used_forearm_bounding_box_max_value = maxForearm;
+    res.used_elbow_bounding_box_min_value = minElbow;
+    res.used_elbow_bounding_box_max_value = maxElbow;
+}
+
+bool SegmentationServices::filter(const float* xyz16, size_t n, const pitt_msgs::ArmFilter::Request& req,
+                                  pitt_msgs::ArmFilter::Response& res, float* xyz16_out, int64_t* n_out,
+                                  int64_t removed[4], pitt_crop_box boxes_out[4]) {
+    pitt_crop_box boxes[4];
+    int64_t rem[4] = {0, 0, 0, 0};
+    armBoxes(req, res, boxes);
+    status_ = PITT_OK;
+    if (!tfError) {  // four CropBox filters with setNegative(true) in a row (:134-141)
+        status_ = pitt_crop_boxes_host(ctx_, xyz16, (int64_t)n, boxes, 4, 1, req.is_dense ? 1 : 0, xyz16_out, n_out, rem);
+    } else {  // :148-152: outputCloud4 = inputCloud
+        if (n > 0 && xyz16_out != xyz16) std::memcpy(xyz16_out, xyz16, n * 16);
+        *n_out = (int64_t)n;
+    }
+    for (int k = 0; k < 4; ++k) {
+        if (removed) removed[k] = rem[k];
+        if (boxes_out) boxes_out[k] = boxes[k];
+    }
+    return true;
+}
+
+bool SegmentationServices::filterDev(const float* x, const float* y, const float* z, int64_t n,
+                                     const pitt_msgs::ArmFilter::Request& req, pitt_msgs::ArmFilter::Response& res,
+                                     float* ox, float* oy, float* oz, int64_t* n_out, int64_t removed[4],
+                                     pitt_crop_box boxes_out[4]) {
+    pitt_crop_box boxes[4];
+    int64_t rem[4] = {0, 0, 0, 0};
+    armBoxes(req, res, boxes);
+    // a transform error returns the input cloud: no stage at all is a copy
+    status_ = pitt_crop_boxes(ctx_, x, y, z, n, boxes, tfError ? 0 : 4, 1, req.is_dense ? 1 : 0, ox, oy, oz, n_out, rem);
+    for (int k = 0; k < 4; ++k) {
+        if (removed) removed[k] = rem[k];
+        if (boxes_out) boxes_out[k] = boxes[k];
+    }
+    return true;
+}
+
+bool SegmentationServices::filter(pitt_msgs::ArmFilter::Request& req, pitt_msgs::ArmFilter::Response& res) {
+    const size_t n = req.input_cloud.size();
+    res.armless_cloud.data.resize(4 * n);
+    int64_t m = 0;
+    const bool ok = filter(req.input_cloud.data.data(), n, req, res, res.armless_cloud.data.data(), &m, nullptr, nullptr);
+    res.armless_cloud.data.resize(status_ < 0 ? 0 : 4 * (size_t)m);
+    return ok;
+}
+
 }  // namespace pitt
 
 // ---- C ABI (pitt_srv.h) -----------------------------------------------------------------------
@@ -846,6 +966,64 @@ int pitt_srv_segment_objects_dev(pitt_srv* s, const float* x, const float* y, co
                                  pitt_scene* out) {
     if (!s || !out || n < 0 || (n > 0 && (!x || !y || !z))) return PITT_E_INVALID;
     return s->svc.segmentObjectsDev(x, y, z, n, out);
+}
+
+int pitt_srv_quaternion_rpy(const double q[4], double rpy[3]) {
+    if (!q || !rpy) return PITT_E_INVALID;
+    pitt::SegmentationServices::quaternionToRPY(q, rpy[0], rpy[1], rpy[2]);
+    return PITT_OK;
+}
+
+namespace {
+// the flat request and poses into the mirror's request and TF state
+void arm_setup(pitt_srv* s, const pitt_srv_arm_request* r, const pitt_srv_arm_pose poses[4], int32_t dense,
+               int32_t tf_error, pitt_msgs::ArmFilter::Request& req) {
+    auto vec = [](int32_t n, const float* v) {
+        return std::vector<float>(v, v + std::min(std::max(n, 0), 8));
+    };
+    req.forearm_bounding_box_min_value = vec(r->n_forearm_min, r->forearm_min);
+    req.forearm_bounding_box_max_value = vec(r->n_forearm_max, r->forearm_max);
+    req.elbow_bounding_box_min_value = vec(r->n_elbow_min, r->elbow_min);
+    req.elbow_bounding_box_max_value = vec(r->n_elbow_max, r->elbow_max);
+    req.is_dense = dense != 0;
+    for (int k = 0; k < 4; ++k) {
+        std::memcpy(s->svc.armTransforms[k].origin, poses[k].origin, sizeof(poses[k].origin));
+        std::memcpy(s->svc.armTransforms[k].rotation, poses[k].rotation, sizeof(poses[k].rotation));
+    }
+    s->svc.tfError = tf_error != 0;
+}
+void arm_used(const pitt_msgs::ArmFilter::Response& res, float used_out[12]) {
+    if (!used_out) return;
+    const std::vector<float>* v[4] = {&res.used_forearm_bounding_box_min_value, &res.used_forearm_bounding_box_max_value,
+                                      &res.used_elbow_bounding_box_min_value, &res.used_elbow_bounding_box_max_value};
+    for (int k = 0; k < 4; ++k)
+        for (int c = 0; c < 3; ++c) used_out[3 * k + c] = (*v[k])[(size_t)c];
+}
+}  // namespace
+
+int pitt_srv_arm_filter(pitt_srv* s, const float* xyz16, int64_t n, int32_t dense, const pitt_srv_arm_request* r,
+                        const pitt_srv_arm_pose poses[4], int32_t tf_error, float* xyz16_out, int64_t* n_out,
+                        float used_out[12], int64_t removed[4], pitt_crop_box boxes_out[4]) {
+    if (!s || n < 0 || (n > 0 && (!xyz16 || !xyz16_out)) || !r || !poses || !n_out) return PITT_E_INVALID;
+    pitt_msgs::ArmFilter srv;
+    arm_setup(s, r, poses, dense, tf_error, srv.request);
+    const bool ok = s->svc.filter(xyz16, (size_t)n, srv.request, srv.response, xyz16_out, n_out, removed, boxes_out);
+    if (s->svc.last_status() < 0) return s->svc.last_status();
+    arm_used(srv.response, used_out);
+    return ok ? 1 : 0;
+}
+
+int pitt_srv_arm_filter_dev(pitt_srv* s, const float* x, const float* y, const float* z, int64_t n, int32_t dense,
+                            const pitt_srv_arm_request* r, const pitt_srv_arm_pose poses[4], int32_t tf_error,
+                            float* ox, float* oy, float* oz, int64_t* n_out, float used_out[12], int64_t removed[4],
+                            pitt_crop_box boxes_out[4]) {
+    if (!s || !r || !poses || !n_out) return PITT_E_INVALID;
+    pitt_msgs::ArmFilter srv;
+    arm_setup(s, r, poses, dense, tf_error, srv.request);
+    const bool ok = s->svc.filterDev(x, y, z, n, srv.request, srv.response, ox, oy, oz, n_out, removed, boxes_out);
+    if (s->svc.last_status() < 0) return s->svc.last_status();
+    arm_used(srv.response, used_out);
+    return ok ? 1 : 0;
 }
 
 int pitt_srv_resolved_params(pitt_srv* s, pitt_support_params* sp, pitt_cluster_params* cp) {

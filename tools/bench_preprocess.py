@@ -4,6 +4,9 @@ unpacking, deepFiltering and transformPointCloud over a 256-frame batch of synth
 algorithmic bytes and the fraction of the 8 TB/s HBM peak, plus a CPU (oracle) sample for scale.
 
     python tools/bench_preprocess.py [--frames 256] [--reps 10]
+
+--crop-box-only runs just the crop-box rows (the arm filter's four default boxes on one 640x480 frame and
+on the 1.2M-point fused scene, with the deep filter on the same clouds in the same run).
 """
 import argparse
 import json
@@ -22,11 +25,77 @@ import pitt_object_table_segmentation_amd as pitt  # noqa: E402
 PEAK = 8000.0  # GB/s, MI355X HBM3E spec
 
 
+def _kernel_rows(ctx, names, extra=None):
+    rows, total_us, total_bytes = {}, 0.0, 0.0
+    for k in names:
+        launches, ms, algo = ctx.profile_get(k)
+        per = ms / launches * 1e3
+        byts = algo / launches + (extra or {}).get(k, 0.0)
+        rows[k] = {"avg_us": round(per, 2), "algorithmic_bytes": byts, "GB_s": round(byts / per / 1e3, 1),
+                   "frac": round(byts / per / 1e3 / PEAK, 4)}
+        total_us += per
+        total_bytes += byts
+    rows["sum"] = {"avg_us": round(total_us, 2), "algorithmic_bytes": total_bytes,
+                   "GB_s": round(total_bytes / total_us / 1e3, 1), "frac": round(total_bytes / total_us / 1e3 / PEAK, 4)}
+    return rows
+
+
+def crop_box_rows(ctx, reps):
+    """pitt_crop_boxes with the arm filter's four default boxes (arm_filter_srv.cpp:32-35) at poses that cut
+    into the cloud (each box centred on a point of it), on one camera frame and on the fused scene; the deep
+    filter on the same cloud in the same run for scale.  Per kernel: HIP-event time and achieved bytes/s
+    against the algorithmic bytes (12 B read per point, 12 B written per kept point, the 1-bit mask written
+    and read once); per call: wall time including the host's wait for the counts."""
+    forearm = ((-0.040, -0.120, -0.190), (0.340, 0.120, 0.105))
+    elbow = ((-0.090, -0.135, -0.160), (0.440, 0.135, 0.110))
+    rpys = ((0.3, -0.4, 0.2), (-0.2, 0.5, 1.1), (0.7, 0.1, -0.6), (-0.5, -0.3, 0.4))
+    out = {}
+    for name, (x, y, z) in (("frame_640x480", pitt.synth_frame(0, 1000)), ("fused_4x640x480", pitt.synth_fused(1000, 4))):
+        n = len(x)
+        fin = np.flatnonzero(np.isfinite(z))
+        at = fin[(len(fin) * np.array([0.3, 0.45, 0.6, 0.75])).astype(int)]
+        boxes = [pitt.crop_box(mn, mx, translation=(x[i], y[i], z[i]), rpy=r)
+                 for (mn, mx), i, r in zip((forearm, forearm, elbow, elbow), at, rpys)]
+        dev = [torch.from_numpy(a).cuda() for a in (x, y, z)]
+        row = {"points": n}
+        for what, call, names in (
+                ("crop_boxes", lambda: ctx.crop_boxes(*dev, boxes), ("k_crop_mark", "k_crop_scan", "k_crop_write")),
+                ("deep_filter", lambda: ctx.deep_filter(*dev), ("k_deep_count", "k_scan_pair", "k_deep_write"))):
+            res = call()  # warm-up (buffers)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                call()
+            torch.cuda.synchronize()
+            wall = (time.perf_counter() - t0) * 1e6 / reps
+            ctx.profile(True)
+            ctx.profile_reset()
+            for _ in range(reps):
+                call()
+            torch.cuda.synchronize()
+            if what == "crop_boxes":
+                kept, extra = int(res[0][0].numel()), None
+                row[what] = {"kept": kept, "removed": [int(v) for v in res[1]]}
+            else:  # k_deep_write's record holds its reads only: add the 12 B written per kept point
+                kept = int(res[0][0].numel()) + int(res[1][0].numel())
+                extra = {"k_deep_write": 12.0 * kept}
+                row[what] = {"kept": kept}
+            row[what].update({"wall_us_per_call": round(wall, 1), "kernels": _kernel_rows(ctx, names, extra)})
+            ctx.profile(False)
+        out[name] = row
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--crop-box-only", action="store_true")
     args = ap.parse_args()
+    if args.crop_box_only:
+        with pitt.Context(0) as ctx:
+            print(json.dumps({"workload": f"crop box rows, {args.reps} reps", "crop_box": crop_box_rows(ctx, args.reps)}))
+        return
     n1 = 640 * 480
     x = np.empty(args.frames * n1, np.float32)
     y = np.empty_like(x)
@@ -190,6 +259,7 @@ def main():
                                                "avg_us": round(ms / launches * 1e3, 1)}
                 ctx.profile(False)
                 prim[name][str(ns + no)] = e
+        crop = crop_box_rows(ctx, args.reps)
     import oracle_binding as orc
     t0 = time.perf_counter()
     k = 0
@@ -225,7 +295,7 @@ def main():
     print(json.dumps({"workload": f"{args.frames} x 640x480 synthetic camera clouds ({n} points), deep filter "
                                   f"(th {used}) + transform, PointXYZ unpack, {args.reps} reps", "points": n, "kept": kept,
                       "kernels": res, "cpu_oracle_points_per_s_1thread": round(cpu), "voxel_grid": vox, "normal_estimation": nrm,
-                      "axis_height": axis, "sphere_segment": sph, **prim,
+                      "axis_height": axis, "sphere_segment": sph, **prim, "crop_box": crop,
                       "gpu_points_per_s": round(n / (sum(r["avg_us"] for r in res.values()) * 1e-6))}))
 
 
